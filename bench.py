@@ -7,8 +7,8 @@ ring of R distinct synthetic matrices (W ~ N(0, 0.02^2), RTN int4 g128 by the bu
 quantizer; R >= 64 so 563 MB of codes cannot be served by the 256 MB Infinity Cache), each with
 its own activation row.  One step = one pass over the ring: R products.
 
-Two ways to run that step, both timed in every GEMV run (the headline `--mode`, the other under
-`other_mode`):
+Two ways to run that step (the headline `--mode`; with `--full` the other is timed too and
+reported under `other_mode`):
   batched  (default) the whole ring as ONE strided-batch launch (qlin_gemv_batched_f16: the
            streaming kernel, every output one MFMA chain in k order) — the kernel's HBM
            throughput when the kernel boundary is paid once per ring;
@@ -18,7 +18,15 @@ Two ways to run that step, both timed in every GEMV run (the headline `--mode`, 
 Prints ONE JSON line (rank 0).  value = whole-job dequant-matmul TFLOP/s (sum over ranks: every
 rank streams its own ring, no collective in the data path -> weak scaling).
 
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds every other
+measurement to the same line: the other GEMV mode, the decode-layer line, the pipeline leg (N > 1
+ranks or `--pipeline on`), the pipeline workload's one-process check and the CPU baseline (each
+with its own `--no-...` switch).  `--dump-outputs DIR` writes what the last timed step computed
+(DIR/<name>.npy, float32) so that two builds can be compared output for output: the inputs are
+seeded, the same arguments give the same inputs.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--ring R]
+                       [--full] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -34,6 +42,7 @@ for _p in (ROOT, PKG):
 
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec (MI355X_MICROARCH.md, chip-level table)
 MFMA_F16_PEAK_TFS = 2500.0  # dense fp16/bf16 MFMA spec (no sparsity)
+DUMP_BUDGET_BYTES = 60 * 10**6  # --dump-outputs: all arrays of one run (under 64 MB with headers)
 
 WORKLOADS = {
     # name: (M, N, K, bits, group, ring, kernel, note)
@@ -117,6 +126,29 @@ def _attach_traffic(roof, pmc, algo, launch_products=None):
     roof["traffic_ratio"] = round(t / algo, 4)
 
 
+def dump_outputs(path, arrays, suffix=""):
+    """--dump-outputs: every tensor of `arrays` (name -> tensor) as path/<name><suffix>.npy in
+    float32, an equal share of DUMP_BUDGET_BYTES each.  A larger output is written as a fixed
+    sample of its flattened elements (indices drawn from numpy RandomState(0): the same for every
+    run and every build).  Returns name -> {shape, written, sampled} for the result line."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // (4 * max(1, len(arrays)))
+    info = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        n = t.numel()
+        if n > cap:
+            idx = torch.from_numpy(np.random.RandomState(0).randint(0, n, size=cap))
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
+        info[name + suffix] = {"shape": list(arrays[name].shape), "written": int(a.size),
+                               "sampled": n > cap}
+    return info
+
+
 def parse():
     ap = argparse.ArgumentParser()
     # default: the launcher's WORLD_SIZE (torchrun without --gpus), else 1
@@ -126,6 +158,14 @@ def parse():
     ap.add_argument("--workload", default="gemv_int4_g128",
                     choices=sorted(WORKLOADS) + [PIPE_WORKLOAD])
     ap.add_argument("--ring", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the other GEMV "
+                         "mode, the decode-layer line, the pipeline leg and its one-process "
+                         "check, the CPU baseline (default: the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as "
+                         "DIR/<name>.npy (float32; a fixed seeded sample of an output too large "
+                         f"for {DUMP_BUDGET_BYTES // 10**6} MB in all)")
     ap.add_argument("--split", action="store_true",
                     help="strong scaling: every rank streams rows [r*N/P, (r+1)*N/P) of the SAME "
                          "ring (output-feature sharding, SURVEY.md §8(e)); default: weak scaling, "
@@ -133,8 +173,8 @@ def parse():
     ap.add_argument("--mode", choices=("batched", "launches"), default="batched",
                     help="GEMV workloads: 'batched' = the whole ring as one strided-batch launch "
                          "(qlin_gemv_batched_f16); 'launches' = one dependent launch per matrix "
-                         "(the decode chain's per-launch cost); the other mode is timed too and "
-                         "reported beside it")
+                         "(the decode chain's per-launch cost); with --full the other mode is "
+                         "timed too and reported beside it")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--ramp-s", type=float, default=0.3,
                     help="untimed seconds of runs before the warmup steps (GPU clock ramp)")
@@ -147,9 +187,9 @@ def parse():
     ap.add_argument("--decode-layers", type=int, default=8)
     ap.add_argument("--decode-kv", type=int, default=512)
     ap.add_argument("--pipeline", choices=("auto", "on", "off"), default="auto",
-                    help="the configs[4] pipeline leg (32 LLaMA3-8B layers as N stages, RCCL "
-                         "send / recv): auto = with N > 1 ranks or --workload "
-                         f"{PIPE_WORKLOAD}")
+                    help="the configs[4] pipeline leg of a --full run (32 LLaMA3-8B layers as N "
+                         "stages, RCCL send / recv): auto = with N > 1 ranks; --workload "
+                         f"{PIPE_WORKLOAD} times it as the headline")
     ap.add_argument("--pipe-layers", type=int, default=32)
     ap.add_argument("--pipe-tokens", type=int, default=2048, help="tokens per PPL window")
     ap.add_argument("--pipe-windows", type=int, default=0,
@@ -468,7 +508,10 @@ def pipeline_bench(args, dev, world, rank, backend):
                       "tokens_per_s": round(world / step_s, 1),
                       "timing": (f"({n_long} - {n_short}) step difference of two generations, "
                                  "max over ranks")}}
-    if not args.pipe_no_check:
+    if args.dump_outputs and rank == 0 and args.workload == PIPE_WORKLOAD:
+        out["outputs"] = dump_outputs(args.dump_outputs, {"pipeline_window_nll": nll,
+                                                          "pipeline_decode_tokens": toks})
+    if args.full and not args.pipe_no_check:
         # the one-process reference on rank 0 (every other rank waits at the barrier)
         ok = torch.zeros(2, dtype=torch.int64, device=dev if backend == "nccl" else "cpu")
         if rank == 0:
@@ -687,6 +730,17 @@ def main():
     G = graph_steps(args.steps) if use_graph else 1
     elapsed, wall = timed(make_runner(step_batched if batched else step_launches, G),
                           args.steps // G, max(1, -(-args.warmup // G)))
+    dumped = None
+    if args.dump_outputs:
+        # the last timed step's results, before anything else writes the output buffers: the
+        # batch's y[R, M, N]; in the launches mode the ring's last len(ys) products
+        if batched:
+            res = {"y": yb}
+        elif len(ys) == 1:
+            res = {"y": ys[0][None]}
+        else:
+            res = {"y": torch.stack([ys[i % len(ys)] for i in range(R - len(ys), R)])}
+        dumped = dump_outputs(args.dump_outputs, res, f"_rank{rank}" if world > 1 else "")
 
     flops = 2.0 * M * N * K
     nbytes = algo_bytes(M, N, K, bits, group)
@@ -727,7 +781,7 @@ def main():
                           if use_graph else
                           "HIP events over the timed region / launches (eager)")
     other = None
-    if kernel == "gemv" and not args.no_other_mode:
+    if args.full and kernel == "gemv" and not args.no_other_mode:
         # the other mode, timed the same way, reported beside the headline
         o_steps = max(5, args.steps // 2)
         oG = graph_steps(o_steps) if use_graph else 1
@@ -762,14 +816,17 @@ def main():
         "roofline": roof,
         "wall_s": round(wall, 4),
     }
+    if dumped is not None:
+        out["outputs"] = dumped
     if other is not None:
         out["other_mode"] = other
-    if kernel == "gemv" and args.workload == "gemv_int4_g128" and not args.no_decode_layer:
+    full = args.full  # everything below takes runs of its own: not part of a plain run
+    if full and args.workload == "gemv_int4_g128" and not args.no_decode_layer:
         out["decode_layer"] = decode_layer_bench(args, dev, timed)
-    if args.pipeline == "on" or (args.pipeline == "auto" and world > 1):
+    if full and (args.pipeline == "on" or (args.pipeline == "auto" and world > 1)):
         # configs[4]: the 32-layer pipeline over the same ranks (RCCL P2P between stages)
         out["pipeline"] = pipeline_bench(args, dev, world, rank, backend)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(M, N, K, bits, group, args.cpu_seconds) \
             if M <= 64 else cpu_baseline(min(M, 32), N, K, bits, group, args.cpu_seconds)
     if rank == 0:

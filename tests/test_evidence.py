@@ -92,6 +92,27 @@ def test_bench_never_publishes_traffic_below_algorithmic_bytes():
     assert r["traffic"] == 119700000 and 1.0 <= r["traffic_ratio"] <= 1.1
 
 
+def test_bench_dump_outputs_is_float32_within_budget_and_repeatable(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy per output; an output over its share of the budget is written
+    as the same seeded sample of its elements on every call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 4 * 100)  # 100 elements per array
+    small = torch.arange(60, dtype=torch.float16).reshape(3, 20)
+    big = torch.arange(1000, dtype=torch.float16).reshape(10, 100)
+    info = bench.dump_outputs(str(tmp_path / "a"), {"small": small, "big": big})
+    bench.dump_outputs(str(tmp_path / "b"), {"small": small, "big": big})
+    s, b = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.float().numpy())
+    assert b.dtype == np.float32 and b.shape == (100,) and len(set(b.tolist())) > 50
+    assert np.array_equal(b, np.load(tmp_path / "b" / "big.npy"))
+    assert info["small"] == {"shape": [3, 20], "written": 60, "sampled": False}
+    assert info["big"] == {"shape": [10, 100], "written": 100, "sampled": True}
+    assert s.nbytes + b.nbytes <= bench.DUMP_BUDGET_BYTES
+
+
 def _newest(pattern):
     files = sorted(glob.glob(os.path.join(ROOT, "profiles", pattern)))
     assert files, pattern

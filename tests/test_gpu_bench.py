@@ -29,6 +29,41 @@ def _bench(*args, extra_env=None, timeout=600):
     return json.loads(lines[0])
 
 
+def test_bench_plain_run_times_the_steps_only_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) measures nothing beside its headline figure, and --dump-outputs
+    writes the last timed step's y[R, 1, N] as float32: the products of the bench's seeded inputs
+    (matrix i from generator seed i, RTN int4 g128; the activation rows from seed 1234),
+    recomputed here in float64 on the quantizer's W_dq, to the fp16-output tolerance of
+    helpers.assert_close_to_ref."""
+    import numpy as np
+    import torch
+    from helpers import assert_close_to_ref
+    from quant import qlin
+    R, N, K = 2, 4096, 4096
+    d = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--ring", str(R), "--ramp-s", "0.05",
+               "--dump-outputs", str(tmp_path / "out"), timeout=120)
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "TFLOP/s" and d["higher_is_better"] is True and d["dtype"] == "f16"
+    for k in ("other_mode", "decode_layer", "pipeline", "cpu_baseline"):
+        assert k not in d, k
+    assert sorted(os.listdir(tmp_path / "out")) == ["y.npy"]
+    y = np.load(tmp_path / "out" / "y.npy")
+    assert y.dtype == np.float32 and y.shape == (R, 1, N)
+    assert d["outputs"]["y"] == {"shape": [R, 1, N], "written": R * N, "sampled": False}
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev)
+    wdq = []
+    for i in range(R):
+        gen.manual_seed(i)
+        w = torch.empty(N, K, device=dev, dtype=torch.float16).normal_(0.0, 0.02, generator=gen)
+        wdq.append(qlin.quantize(w, 4, 128, 0, want_params=False)["x_dq"].double())
+    gen.manual_seed(1234)
+    xs = torch.empty(R, 1, K, device=dev, dtype=torch.float16).normal_(0.0, 1.0, generator=gen)
+    for i in range(R):
+        ref = (xs[i].double() @ wdq[i].T).cpu().numpy()
+        assert_close_to_ref(y[i], ref, what=f"product {i}")
+
+
 @pytest.mark.timeout(900)
 @pytest.mark.parametrize("split", [False, True])
 def test_bench_gpus2_spawns_ranks(split):
@@ -59,9 +94,9 @@ def test_bench_gpus2_pipeline_leg():
     RCCL over xGMI, one rank per GPU, in the driver's runs), windows in flight and graph-replayed
     decode steps are timed, and the pipeline's NLL and greedy tokens equal one process bit for
     bit."""
-    d = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--ring", "8", "--ramp-s", "0.05",
-               "--no-cpu-baseline", "--no-decode-layer", "--no-other-mode", "--pipe-windows", "2",
-               "--pipe-decode", "8", extra_env={"BENCH_DIST_BACKEND": "gloo",
+    d = _bench("--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--ring", "8", "--ramp-s",
+               "0.05", "--no-cpu-baseline", "--no-decode-layer", "--no-other-mode",
+               "--pipe-windows", "2", "--pipe-decode", "8", extra_env={"BENCH_DIST_BACKEND": "gloo",
                                                  "BENCH_SHARE_GPU": "1"}, timeout=1000)
     assert d["n_gpus"] == 2
     p = d["pipeline"]

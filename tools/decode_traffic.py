@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """HBM bytes per decode layer from a rocprofv3 --pmc FETCH_SIZE pass over bench.py's decode-layer
-line (run with --no-other-mode --ramp-s 0).
+line (run with --full --no-other-mode --ramp-s 0).
 
 Every dispatch of the layer pass counts, whatever its kernel is called (an
 allow-list of kernel names missed the round-5 gate/up kernel and published half the bytes).  The
@@ -75,7 +75,7 @@ def layer_windows(rows):
     # left out, never mixed in
     if count < 0.8 * len(wins):
         raise SystemExit(f"layer windows of different lengths {dict(shapes)}: no dominant decode "
-                         "pass (run bench.py with --no-other-mode)")
+                         "pass (run bench.py with --full --no-other-mode)")
     wins = [w for w in wins if len(w) == n]
     if n < len(classes):
         raise SystemExit(f"{n} dispatches per layer: fewer than the {len(classes)} kernel classes "
@@ -111,7 +111,7 @@ def main():
            "correction": "FETCH_SIZE KiB x 1024 x 2 (gfx950 counts half of wide streaming reads)",
            "method": ("every dispatch of each layer window (the q/k/v dispatch before an attention "
                       "dispatch up to the next layer's q/k/v), dispatch order; mean over windows"),
-           "source": "rocprofv3 --pmc FETCH_SIZE, separate pass, bench.py --no-other-mode",
+           "source": "rocprofv3 --pmc FETCH_SIZE, separate pass, bench.py --full --no-other-mode",
            "excluded": ("windows of another length (the eager warm-up pass before the graph "
                         "capture, which also runs host-side torch ops)")}
     with open(out, "w") as fh:

@@ -12,7 +12,7 @@ timeout -k 10 700 python -u -m pytest ${TESTS:-tests/test_gpu_attn.py tests/test
   -m gpu -v -p no:cacheprovider --timeout 300 --timeout-method thread > "$OUT/${T}_tests.log" 2>&1
 rc=$?; echo "tests rc=$rc"; grep -E "passed|failed" "$OUT/${T}_tests.log" | tail -2; grep FAILED "$OUT/${T}_tests.log" | head
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/${T}_bench.log" 2>&1
+timeout -k 10 300 python bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/${T}_bench.log" 2>&1
 rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || exit $rc
 python3 - "$OUT/${T}_bench.log" <<'PY'
 import json, sys

@@ -20,13 +20,13 @@ step() {  # name, timeout, command...
 PHASE=${PHASE:-all}
 ring_of() { case $1 in *int2*) echo 96 ;; *) echo 64 ;; esac; }  # bench.py WORKLOADS ring
 if [ "$PHASE" != 2 ]; then
-step bench_gemv_int4_g128 300 python bench.py
+step bench_gemv_int4_g128 300 python bench.py --full
 for w in ${WORKLOADS:-gemv_int3_g64 gemv_int2_g64 gemv_int3_g64_hqq gemv_int2_g64_hqq gemm_int4_g128_m32 gemm_int4_g128_m2048 gemm_int4_g128_m65536 gemm_int4_g64_hqq_m2048}; do
-  step bench_$w 300 python bench.py --workload $w --no-cpu-baseline
+  step bench_$w 300 python bench.py --full --workload $w --no-cpu-baseline
 done
 export TMPDIR=/tmp
 (cd /tmp && step kernel_trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o run \
-   -- python "$ROOT/bench.py" --steps 10 --warmup 2 --no-cpu-baseline) || exit $?
+   -- python "$ROOT/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline) || exit $?
 find "$OUT/kt" -name "*kernel_stats.csv" -exec cp {} "$OUT/${R}_gemv_int4_g128_kernel_stats.csv" \;
 # FETCH_SIZE per dispatch, one pass per mode: the batched streaming launch (headline) and the
 # dependent single launches (other_mode)
@@ -73,7 +73,7 @@ if [ "$PHASE" != 1 ]; then
 export TMPDIR=/tmp
 # the decode layer's traffic: every GEMV / attention dispatch of a --no-other-mode run
 (cd /tmp && step pmc_decode 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmcd" -o run \
-   -- python "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-other-mode --ramp-s 0) \
+   -- python "$ROOT/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-other-mode --ramp-s 0) \
    || exit $?
 python tools/decode_traffic.py "$OUT/pmcd" "$OUT/${R}_decode_layer_int4_g128_pmc.json"
 step decode_layer 300 python tools/bench_decode.py
@@ -86,10 +86,10 @@ step attn_prefill 300 python tools/dev/attn_prefill_bench.py
 cp "$OUT/attn_prefill.out" "$OUT/${R}_attn_prefill.txt"
 # configs[4]: the 32-layer pipeline leg, one rank (the driver's multi-GPU runs: RCCL, one rank per
 # GPU), and its two-rank rehearsal on one GPU (gloo)
-step pipeline_n1 600 python bench.py --workload pipeline_llama3_8b_int4_g128
+step pipeline_n1 600 python bench.py --full --workload pipeline_llama3_8b_int4_g128
 tail -1 "$OUT/pipeline_n1.out" > "$OUT/${R}_pipeline_n1.bench.json"
 export BENCH_DIST_BACKEND=gloo BENCH_SHARE_GPU=1
-step pipeline_n2_gloo 900 python bench.py --gpus 2 --steps 4 --warmup 1 --ring 8 --no-cpu-baseline \
+step pipeline_n2_gloo 900 python bench.py --full --gpus 2 --steps 4 --warmup 1 --ring 8 --no-cpu-baseline \
   --no-decode-layer --no-other-mode --pipe-windows 4
 unset BENCH_DIST_BACKEND BENCH_SHARE_GPU
 tail -1 "$OUT/pipeline_n2_gloo.out" > "$OUT/${R}_pipeline_n2_gloo_rehearsal.bench.json"
